@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W                      (BASELINE.json config 2, the headline)
     python bench.py --config cfg4 --steps 64                           (config 4: K full SonicSet scenes per rank + gather of the mixes)
+    python bench.py ... --dump-outputs DIR                             (+ the last timed step's outputs as DIR/<name>.npy)
     (N > 1: either plain `python bench.py --gpus N` -- it starts the ranks itself -- or python -m torch.distributed.run --nnodes=1
      --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
@@ -360,6 +361,31 @@ def emit(full, detail_dir=None):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs DIR: what the timed path returned in its last timed step, one DIR/<name>.npy per array, float32 (float64 stays
+    float64).  An array over its share of the 64 MB limit is written as a fixed sample: the same seeded, sorted flat indices in every run
+    with the same arguments, so that two builds compare output for output.  Returns {name: what was written}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // max(1, len(arrays))      # (4 KiB per file for the .npy header)
+    written = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        rec = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+            rec["sample"] = f"{a.size} of {int(np.prod(rec['shape']))} elements (flat indices: sorted numpy default_rng(1234).choice without replacement)"
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name] = rec
+    print(f"[bench] dump-outputs -> {directory}: " + json.dumps(written), file=sys.stderr, flush=True)
+    return written
+
+
 # ------------------------------------------------------------------------------------------------ CPU legs (rank 0, N = 1)
 def cpu_baselines(sc, seg, bank_h, budget_s, all_cores=True):
     import numpy as np
@@ -593,6 +619,8 @@ def run_cfg2(args, rank, local_rank, world, dev):
         if world > 1:
             dist.barrier()
         dt = time.perf_counter() - t0
+        if sg is not None and y is not None and rank == 0 and getattr(args, "dump_outputs", None):
+            y = y.clone()                      # (untimed, --dump-outputs: the last step may have rendered into a gather slot, which close() frees)
         if hasattr(sg, "close"):
             sg.close()                         # (untimed: the IPC gather's array goes back; collective, like its creation)
         return parallel.barrier_max_seconds(dt, device=dev), y
@@ -652,6 +680,8 @@ def run_cfg2(args, rank, local_rank, world, dev):
         rec, yy = window(ev)
         (ev_windows if ev else windows).append(rec)
         y = yy
+    # --dump-outputs: the last timed step's y (a scratch buffer, or timed()'s copy of a gather slot), copied before the renders below reuse it
+    y_dump = y.clone() if getattr(args, "dump_outputs", None) and rank == 0 else None
     serial_windows = []
     if overlap:                                  # the one-stream step (= the latency of a single render: spectra launch + render launch) beside the throughput figure
         for _ in range(3):
@@ -840,6 +870,8 @@ def run_cfg2(args, rank, local_rank, world, dev):
         num = float(np.sqrt(np.mean((yg.astype(np.float64) - yref) ** 2)))
         den = float(np.sqrt(np.mean(yref.astype(np.float64) ** 2)))
         out["parity_rel_rms_vs_oracle"] = num / den
+    if y_dump is not None:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, {"y": y_dump})
     return out
 
 
@@ -890,7 +922,8 @@ def run_scenes(args, rank, local_rank, world, dev):
             sir, snr = draws(base + j)
             has_next = j + 1 < k and not (sg is not None and sg.on and sg.scene(j + 1) is None)
             nxt = (pl[(j + 1) % len(pl)], base + j + 1) if has_next and not os.environ.get("BENCH_NO_PREFETCH") else None
-            gains.append(rend.render(spec, seed=base + j, sirs=sir, snr=snr, out=out, sync=False, next_scene=nxt)[1])      # (5,) float64 on the device: no wait per scene
+            run.last = rend.render(spec, seed=base + j, sirs=sir, snr=snr, out=out, sync=False, next_scene=nxt)             # (mix, gains)
+            gains.append(run.last[1])                                   # (5,) float64 on the device: no wait per scene
             if sg is not None:
                 sg.submit(j)
             if os.environ.get("BENCH_SCENE_EVENTS"):                       # (lab: per-scene GPU and host times of the loop)
@@ -921,11 +954,15 @@ def run_scenes(args, rank, local_rank, world, dev):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     run.evs = []
+    run.last = None
     res = run(per_rank, sg, lo)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = parallel.barrier_max_seconds(time.perf_counter() - t0, device=dev)
+    # --dump-outputs: the last timed scene's mix and loudness gains, copied before the renders below reuse the renderer's buffers
+    last_dump = ({"mix": run.last[0].clone(), "lufs_gains": run.last[1].clone()}
+                 if getattr(args, "dump_outputs", None) and rank == 0 and getattr(run, "last", None) is not None else None)
     if os.environ.get("BENCH_SCENE_EVENTS") and run.evs:
         ge = [a[0].elapsed_time(b[0]) * 1e3 for a, b in zip(run.evs[:-1], run.evs[1:])]
         he = [(b[1] - a[1]) * 1e6 for a, b in zip(run.evs[:-1], run.evs[1:])]
@@ -1086,6 +1123,7 @@ def run_scenes(args, rank, local_rank, world, dev):
     cpu = None
     if world == 1 and getattr(args, "cpu_seconds", 0) > 0:
         cpu = cpu_scene_chain(spec, rend, dev, getattr(args, "cfg2_cpu_seconds", None), audio_s)
+    dumped = dump_outputs(args.dump_outputs, last_dump) if last_dump is not None else None
     return {
         "metric": "scene-sec/sec (full SonicSet sample: 3 moving + 2 static renders + LUFS + mix, 8-mic, 60 s @ 16 kHz)",
         "value": total * audio_s / dt,
@@ -1109,6 +1147,7 @@ def run_scenes(args, rank, local_rank, world, dev):
         "gather_verification": verify,
         "cfg3_no_gather": cfg3,
         "scene_launch_same_bits_as_separate_renders": scene_bits,
+        "dumped_outputs": dumped,
     }
 
 
@@ -1471,6 +1510,7 @@ def secondary_legs(args, rank, local_rank, dev, primary):
     def cfg5():
         a = copy.copy(args)
         a.config, a.steps, a.warmup, a.windows, a.event_windows, a.no_ab = "cfg5", 10, 2, 3, 2, True
+        a.dump_outputs = None                                  # (the headline's outputs only)
         a.cpu_seconds = min(args.cpu_seconds, 12.0)
         o = run_cfg2(a, rank, local_rank, 1, dev)
         for k in ("clocks",):
@@ -1482,6 +1522,7 @@ def secondary_legs(args, rank, local_rank, dev, primary):
         a.config, a.steps, a.warmup = "cfg4", 64, 16     # (16 untimed scenes: the host runs several scenes ahead of the GPU at first and grows its ring of pinned
                                                           #  plan buffers -- ~1 ms of hipHostMalloc each, scenes 3-5 of a 2-scene warm-up -- and the clocks take
                                                           #  ~15 ms of scenes to settle: 1.05 ms per scene at first, 0.92 sustained; profiles/r06ax)
+        a.dump_outputs = None                                  # (the headline's outputs only)
         cb = (primary.get("cpu_baseline") or {})
         a.cfg2_cpu_seconds = cb.get("seconds_measured") if "whole config" in str(cb.get("sample", "")) else None
         return run_scenes(a, rank, local_rank, 1, dev)
@@ -1554,7 +1595,12 @@ def main():
     ap.add_argument("--scene-config", default=None, help="cfg3 / cfg4: shapes of a scene's sources (default cfg2; 'tiny' for dry runs)")
     ap.add_argument("--legs", default=None, help="secondary legs of the default run, comma separated, in this order: host,cfg5,cfg4,cfg1,batch,real (default: all)")
     ap.add_argument("--lib", default=os.environ.get("BENCH_LIB"), help="measurement tools: another build of the library (tuning / A-B variants)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a larger output is written as a fixed seeded sample); the inputs are the same in every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1 (the number of timed steps)")
     if args.lib:
         from sonicsim_amd import _lib
         _lib.use_library(args.lib)

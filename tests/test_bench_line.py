@@ -97,3 +97,22 @@ def test_emit_prints_details_first_and_the_headline_last(tmp_path):
     # the driver keeps the tail of stdout: the headline must sit entirely inside the last 8 KB
     tail = buf.getvalue()[-8192:]
     assert json.loads(tail.splitlines()[-1])["value"] == json.loads(line)["value"]
+
+
+def test_dump_outputs_float_files_under_the_limit(tmp_path):
+    """--dump-outputs: one .npy per returned array, float32 / float64; an output over its share of 64 MB becomes a fixed seeded sample"""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(0)
+    small = torch.from_numpy(rng.standard_normal((8, 1000)).astype(np.float32))
+    gains = torch.from_numpy(rng.standard_normal(5))                                  # float64 stays float64
+    big = np.arange(2 * 5_000_000, dtype=np.float64).reshape(2, 5_000_000)            # 80 MB: over the limit on its own
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"y": small, "gains": gains, "big": big})
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_LIMIT_BYTES == 64 << 20
+    y, g, b = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("y", "gains", "big"))
+    assert y.dtype == np.float32 and np.array_equal(y, small.numpy())
+    assert g.dtype == np.float64 and np.array_equal(g, gains.numpy())
+    assert b.dtype == np.float64 and b.ndim == 1 and 0 < b.size < big.size
+    assert np.all(np.diff(b) > 0) and np.all(b == np.floor(b))                      # a sorted sample of the flat elements
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))                   # the same sample in every run

@@ -54,14 +54,14 @@ def test_product_never_imports_oracle():
                 assert "/root/reference" not in src
 
 
-def test_compat_aliases_resolve():
+def test_compat_aliases_resolve(tmp_path):
     import subprocess
     import sys
     code = ("import sys; sys.path.insert(0, %r); import SonicSim_moving, SonicSim_audio, SonicSim_rir; "
             "assert SonicSim_moving.interpolate_moving_audio.__module__ == 'sonicsim_amd.SonicSim_moving'; "
             "assert callable(SonicSim_audio.generate_rir_combination) and callable(SonicSim_rir.render_rir_parallel); "
             "import torch; assert not torch.cuda.is_initialized()") % os.path.join(ROOT, "sonicsim_amd", "compat")
-    subprocess.run([sys.executable, "-c", code], check=True, cwd="/tmp")
+    subprocess.run([sys.executable, "-c", code], check=True, cwd=str(tmp_path))      # outside the repository tree
 
 
 def test_signatures_match_reference_contract():
